@@ -30,8 +30,15 @@ Frames: seeded uint8 noise (no Kodak, no checkpoints offline).
 
 Multi-GPU: `--gpus N` relaunches itself under torch.distributed.run (one process per GPU, 127.0.0.1)
 unless WORLD_SIZE is already set.  Images are sharded (every rank codes its own batches: weak scaling);
-the only collectives are barriers, a MAX of the timed region and one all_gather of the per-image
+the only collectives are barriers, a MAX of the timed region and, with `--full`, one all_gather of the per-image
 rate/distortion records (RCCL over xGMI).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set up, warm up, time the N
+steps, write the last step's outputs (`--dump-outputs DIR`) and print the line; the roofline of the line comes from the
+timed region's own stamps and events.  Everything measured or checked beside the headline -- the side schedules, the
+gang and sub-stream legs, the quality of the last batch and its comparison with the reference's full-frame fixture, the
+per-image path and the CPU baseline -- runs only with `--full`; their own options (`--side-steps`, `--gang`,
+`--substream-steps`, `--per-image`, `--cpu-budget`) select among them there.
 
 Prints ONE JSON line on rank 0.  Roofline, CPU baseline and PMC definitions: DESIGN.md §6.
 """
@@ -56,6 +63,7 @@ for _p in (ROOT, PKG):
 METRIC = "Mpixels/s encode+decode, B8_lowrate N768M96, 768×768; bpp/PSNR vs ref"
 PEAK_FP32_TFLOPS = 157.3     # MI355X_MICROARCH.md: f32 MFMA (dense) peak
 PEAK_HBM_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E peak (spec)
+DUMP_MAX_ELEMS = 3_000_000   # --dump-outputs: elements written per array (12 MB as float32)
 
 CONFIG_LAMBDA = {"B8_lowrate": 117.045, "B8_highrate": 11704.5, "B4_highrate": 11704.5, "B16_lowrate": 117.045}
 CONFIGS = {   # name -> (B, KS, N, M)
@@ -150,7 +158,19 @@ def parse_args(argv=None):
     ap.add_argument("--per-image", type=int, default=1,
                     help="1: also time the reference's per-image path (eval_model, agents/blkbsdimgcomp_agent.py:591-599: "
                          "compress() then decompress() of ONE frame, batch 1), median of 3")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is reported beside the headline: the side schedules (--side-steps), the gang "
+                         "(--gang) and sub-stream (--substream-steps) legs, the last batch's quality and its comparison "
+                         "with the reference's full-frame fixture, the per-image path (--per-image) and the CPU baseline "
+                         "(--cpu-budget); without it those legs are skipped whatever their options say")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its caller (rank 0's last "
+                         "batch: the encoder's symbols, indexes and reconstruction, the bitstreams and the decoder's "
+                         "reconstruction) as DIR/<name>.npy, float32 / float64; arrays past DUMP_MAX_ELEMS elements as a "
+                         "fixed seeded sample of their elements")
     a = ap.parse_args(argv)
+    if not a.full:
+        a.cpu_budget, a.side_steps, a.gang, a.substream_steps, a.per_image = 0.0, 0, 0, 0, 0
     if a.team_batches == 0:
         a.team_batches = 2 if a.batch <= 16 else 1
     return a
@@ -739,6 +759,8 @@ def main():
     # ---- headline: the reference bitstream format, one 32-frame batch per decode pass
     dt, phase, (r, streams, z), kstats = pipeline(args.steps, depth, prof=True, label="headline", workers=args.workers,
                                                   team=args.team)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r, streams, z)
 
     side = {}
     if args.side_steps > 0 and args.team and args.enc_pass > 1:
@@ -786,22 +808,27 @@ def main():
 
     # ---- quality of the last decoded batch (outside the timed region) + parity against the reference's
     #      full-frame fixture (tests/golden), when this is its configuration
-    bit_exact = bool(torch.equal(z, r["zhat"]))
-    xq = frames_of(max(0, args.steps - 1))
-    sse = ((z - xq) ** 2).double().sum(dim=(1, 2, 3))
-    rec = torch.stack([torch.tensor([float(len(s)) for s in streams], dtype=torch.float64, device=dev), sse,
-                       torch.full((n,), float(H * W * 3), dtype=torch.float64, device=dev)], dim=1)
-    rec, bit_exact = gather_records(rec.to(coll_dev), bit_exact, dist)
-    rec = rec.cpu().numpy()
-    bpp = float(np.mean(rec[:, 0] * 8.0 / (H * W)))
-    psnr = float(np.mean(-10 * np.log10(rec[:, 1] / rec[:, 2])))
-    vs_ref = tq = per_img = None
-    if rank == 0:
-        vs_ref = compare_full_frame_fixture(enc_model, args, arch, dev)
-        if args.side_steps > 0:
-            tq = transform_quality(arch, cfg, dev, H, W)
-        if args.per_image:
-            per_img = per_image_timing(enc_model, dec_models, arch, H, W, dev)
+    quality = per_img = None
+    if args.full:
+        bit_exact = bool(torch.equal(z, r["zhat"]))
+        xq = frames_of(max(0, args.steps - 1))
+        sse = ((z - xq) ** 2).double().sum(dim=(1, 2, 3))
+        rec = torch.stack([torch.tensor([float(len(s)) for s in streams], dtype=torch.float64, device=dev), sse,
+                           torch.full((n,), float(H * W * 3), dtype=torch.float64, device=dev)], dim=1)
+        rec, bit_exact = gather_records(rec.to(coll_dev), bit_exact, dist)
+        rec = rec.cpu().numpy()
+        bpp = float(np.mean(rec[:, 0] * 8.0 / (H * W)))
+        psnr = float(np.mean(-10 * np.log10(rec[:, 1] / rec[:, 2])))
+        vs_ref = tq = None
+        if rank == 0:
+            vs_ref = compare_full_frame_fixture(enc_model, args, arch, dev)
+            if args.side_steps > 0:
+                tq = transform_quality(arch, cfg, dev, H, W)
+            if args.per_image:
+                per_img = per_image_timing(enc_model, dec_models, arch, H, W, dev)
+        quality = {"rate_point": args.rate, "bpp": round(bpp, 5), "psnr_db": round(psnr, 3),
+                   "enc_dec_bit_exact": bit_exact, "images_gathered": int(rec.shape[0]), "vs_ref": vs_ref,
+                   "transform_point": tq}
 
     if rank != 0:
         if dist:
@@ -871,10 +898,7 @@ def main():
                    + "; the timed region holds the compress and decompress of the same batches, fill and drain "
                      "included"},
         "roofline": roof, "cpu_baseline": cpu,
-        "quality": {"rate_point": args.rate, "bpp": round(bpp, 5), "psnr_db": round(psnr, 3),
-                    "enc_dec_bit_exact": bit_exact, "images_gathered": int(rec.shape[0]), "vs_ref": vs_ref,
-                    "transform_point": tq},
-        "per_image": per_img,
+        "full": bool(args.full), "quality": quality, "per_image": per_img,
         "phases_ms_per_step": {k: round(v / args.steps * 1e3, 2) for k, v in phase.items()},
         "step_algorithmic_tflop": round(step_flops / 1e12, 3),
         "step_mfma_frac": round(step_flops / (dt / args.steps) / (PEAK_FP32_TFLOPS * 1e12), 5),
@@ -886,6 +910,31 @@ def main():
     print(json.dumps(out), flush=True)
     if dist:
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(out_dir, r, streams, z):
+    """--dump-outputs: what the last timed step handed back to its caller, one float32 / float64 .npy file per array --
+    the compress record of the batch (symbols and indexes [n, Hb*Wb*M], the encoder's reconstruction zhat
+    [n, Hb, Wb, 3B^2]), its bitstreams (their bytes back to back and their lengths) and the decoder's reconstruction.
+    An array of more than DUMP_MAX_ELEMS elements is written as the elements at sorted flat positions drawn from
+    default_rng(0) for its size (the same positions in every run and build; five such files stay under 64 MB)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def put(name, t):
+        t = t.reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+    put("enc_symbols", r["symbols"])
+    put("enc_indexes", r["indexes"])
+    put("enc_zhat", r["zhat"])
+    put("dec_zhat", z)
+    put("stream_bytes", torch.from_numpy(np.frombuffer(b"".join(bytes(s) for s in streams), dtype=np.uint8).copy()))
+    np.save(os.path.join(out_dir, "stream_lengths.npy"), np.array([len(s) for s in streams], dtype=np.float64))
 
 
 def gather_records(rec, ok, dist):

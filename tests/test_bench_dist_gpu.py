@@ -20,7 +20,8 @@ def test_bench_two_ranks_one_gpu():
     env = dict(os.environ, LBIC_BENCH_DEVICE="0", LBIC_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     n, size, steps = 4, 64, 3
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "2",
+    # --full: the per-image records of the last batch (quality) are gathered only there
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", str(steps), "--warmup", "2",
            "--batch", str(n), "--size", str(size), "--team", "2", "--cpu-budget", "0", "--side-steps", "0",
            "--per-image", "0"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)

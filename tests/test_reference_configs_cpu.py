@@ -15,18 +15,22 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the reference's four configs, shipped verbatim (data) with the package
 REF_CONFIGS = sorted(glob.glob(os.path.join(ROOT, "learned-block-based-image-compression_amd", "configs", "*.json")))
+REF_CONFIG_SHA256 = {   # of the reference's configs/*.json
+    "blkbsdimgcomp_B16_lowrate.json": "e0b1c62c6191074a6c77acbcce27745980d89ea2460906254f0439a9c5bf5bb9",
+    "blkbsdimgcomp_B4_highrate.json": "d39435dfcebb0f212bc66e53dd27cb0bf4f73b294597241dcba359570203f35a",
+    "blkbsdimgcomp_B8_highrate.json": "96550cf2acff6fe7060bbb86aedc1250f8aed152b9c1b11058e65a0c575312fc",
+    "blkbsdimgcomp_B8_lowrate.json": "1e8515aa3954141fb5e0ba8309588d6098b371b62a8ae346ec994d96413f601d",
+}
 
 
 def test_shipped_configs_are_verbatim():
-    """learned-block-based-image-compression_amd/configs/*.json are byte copies of the reference's configs/*.json
-    (compared where /root/reference is present, i.e. not on the GPU box)."""
-    assert len(REF_CONFIGS) == 4
-    ref_dir = "/root/reference/configs"
-    if not os.path.isdir(ref_dir):
-        pytest.skip("reference not present")
+    """learned-block-based-image-compression_amd/configs/*.json are byte copies of the reference's configs/*.json:
+    the SHA-256 of every shipped file equals the digest taken from the reference's own file."""
+    import hashlib
+    assert [os.path.basename(p) for p in REF_CONFIGS] == sorted(REF_CONFIG_SHA256)
     for p in REF_CONFIGS:
-        with open(p, "rb") as a, open(os.path.join(ref_dir, os.path.basename(p)), "rb") as b:
-            assert a.read() == b.read(), p
+        with open(p, "rb") as a:
+            assert hashlib.sha256(a.read()).hexdigest() == REF_CONFIG_SHA256[os.path.basename(p)], p
 
 
 @pytest.mark.parametrize("path", REF_CONFIGS, ids=[os.path.basename(p) for p in REF_CONFIGS])
@@ -171,3 +175,43 @@ def test_bench_team_schedule_defaults():
     assert bench.parse_args(["--batch", "8"]).team_batches == 2
     assert bench.parse_args(["--batch", "24"]).team_batches == 1
     assert bench.parse_args(["--team-batches", "2"]).team_batches == 2
+
+
+def test_bench_plain_run_skips_the_side_legs():
+    """Without --full the legs beside the headline are off whatever their options say; --full keeps the options."""
+    import bench
+    legs = ["--side-steps", "2", "--gang", "2", "--substream-steps", "4", "--per-image", "1", "--cpu-budget", "5"]
+    a = bench.parse_args(legs)
+    assert not a.full
+    assert (a.side_steps, a.gang, a.substream_steps, a.per_image, a.cpu_budget) == (0, 0, 0, 0, 0.0)
+    a = bench.parse_args(["--full"] + legs)
+    assert a.full
+    assert (a.side_steps, a.gang, a.substream_steps, a.per_image, a.cpu_budget) == (2, 2, 4, 1, 5.0)
+    a = bench.parse_args(["--full"])
+    assert (a.side_steps, a.gang, a.substream_steps, a.per_image, a.cpu_budget) == (2, 0, 0, 1, 24.0)
+    assert bench.parse_args(["--steps", "7"]).steps == 7 and bench.parse_args([]).dump_outputs == ""
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 / float64 .npy per array of the last step; an array past DUMP_MAX_ELEMS elements is
+    written as the same seeded sample of its elements in every run."""
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 50)
+    n, L = 2, 40
+    r = dict(symbols=torch.arange(n * L, dtype=torch.int32).reshape(n, L), indexes=torch.ones(n, 10, dtype=torch.int32),
+             zhat=torch.linspace(-1, 1, n * 3 * 4 * 12).reshape(n, 3, 4, 12), bits=None)
+    z = r["zhat"] + 1.0
+    streams = [b"\x01\x02\x03", b"\xff"]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), r, streams, z)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["dec_zhat", "enc_indexes", "enc_symbols", "enc_zhat", "stream_bytes", "stream_lengths"]
+    assert all(v.dtype in (np.float32, np.float64) and v.ndim == 1 for v in got.values())
+    assert list(got["stream_bytes"]) == [1.0, 2.0, 3.0, 255.0] and list(got["stream_lengths"]) == [3.0, 1.0]
+    assert np.array_equal(got["enc_indexes"], np.ones(20, np.float32))           # small arrays whole
+    pos = np.sort(np.random.default_rng(0).integers(0, n * L, 50))
+    assert np.array_equal(got["enc_symbols"], pos.astype(np.float32))            # symbols[i] = i: the sampled positions
+    assert got["enc_zhat"].shape == (50,) and np.array_equal(got["dec_zhat"], got["enc_zhat"] + 1.0)
+    for k, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / (k + ".npy"))), k

@@ -10,7 +10,7 @@ O=$R/gpurun_out
 TAG=${1:-x}
 mkdir -p $O
 cd $R
-B="python3 -u bench.py --cpu-budget 0 --side-steps 0 --per-image 0"
+B="python3 -u bench.py --full --cpu-budget 0 --side-steps 0 --per-image 0"
 timeout -k 10 300 $B --config B8_highrate --size 768 --height 512 --batch 3 --steps 16 --warmup 3 > $O/cfg3_shard_$TAG.log 2>&1
 timeout -k 10 300 $B --config B8_highrate --size 768 --height 512 --batch 24 --steps 8 --warmup 3 > $O/cfg3_all24_$TAG.log 2>&1
 timeout -k 10 500 $B --config B4_highrate --size 768 --batch 32 --steps 16 --warmup 3 > $O/cfg4_$TAG.log 2>&1

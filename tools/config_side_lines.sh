@@ -8,7 +8,7 @@ O=$R/gpurun_out
 TAG=${1:-x}
 mkdir -p $O
 cd $R
-B="python3 -u bench.py --cpu-budget 0 --side-steps 0 --warmup 2 --steps 2"
+B="python3 -u bench.py --full --cpu-budget 0 --side-steps 0 --warmup 2 --steps 2"
 timeout -k 10 300 $B --config B8_highrate --size 768 --height 512 --batch 3 --substream-steps 16 --per-image 1 > $O/cfg3_side_$TAG.log 2>&1
 timeout -k 10 300 $B --config B8_highrate --size 768 --height 512 --batch 24 --substream-steps 8 --per-image 0 > $O/cfg3_all24_side_$TAG.log 2>&1
 timeout -k 10 300 $B --config B4_highrate --size 768 --batch 32 --per-image 1 > $O/cfg4_side_$TAG.log 2>&1
