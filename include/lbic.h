@@ -16,6 +16,25 @@
  *     reference is single-threaded, agents/blkbsdimgcomp_agent.py:565-566).
  *   - Symbols / indexes are int32 in the reference's order: per image, raster block order, latent
  *     channel minor (graphs/models/BlockBasedImgCompLossy_net.py:353-354).
+ *
+ * Environment switches
+ *   Test levers and diagnostics only: every choice a caller needs is an lbc_set_option.  Each is read as an integer at
+ *   every call it affects (absent or empty: the default), so a process may change them between calls.  Every path they
+ *   select produces the same bits.  This list is the whole set (tests/test_lib_cpu.py compares it with the sources).
+ *   LBIC_L0CACHE       0: no layer-0 map cache (KS[1] = 3), read by lbc_create (default 1)        test lever
+ *   LBIC_ENC_FORK      0 / 1: the encoder graph as one chain / forked, over LBC_OPT_ENC_FORK       test lever
+ *   LBIC_RANS_SPARSE   0 / 1: the dense / sparse GPU rANS decoder at any rate (default: by rate);
+ *                      0 also keeps single images off k_dec_one                                    test lever
+ *   LBIC_ONE           0: lbc_decode of one image stays on the row graphs (default 1)              test lever
+ *   LBIC_ONE_TMO       100 MHz ticks one k_dec_one wait may take (default 10^8 = 1 s)              test lever
+ *   LBIC_ONE_STAMPS    1: record lbc_one_stamps                                                    diagnostic
+ *   LBIC_TEAM          0: lbc_decode_team decodes through lbc_decode per batch (default 1)         test lever
+ *   LBIC_TEAM_SPREAD   1, 2, 4, 8: XCD slots per team where the batch count allows                 test lever
+ *   LBIC_TEAM_SC1      1: write-through hand-offs in the team kernel                               test lever
+ *   LBIC_TEAM_TMO      100 MHz ticks one team barrier waits (default 10^8 = 1 s)                   test lever
+ *   LBIC_TEAM_STAMPS   1: record lbc_team_stamps                                                   diagnostic
+ *   LBIC_TEAM_VERBOSE  1: one line per team launch, and per barrier timeout, on stderr             diagnostic
+ *   LBIC_DEBUG_STAMPS  1: the profiler prints its slot range and implausible stamps on stderr      diagnostic
  */
 #ifndef LBIC_H
 #define LBIC_H

@@ -4,7 +4,7 @@
 //                                        [v+2][h+2]; rows -2,-1 and columns -2,-1,Wb,Wb+1 stay zero, so
 //                                        every window gather of the reference (zero pad outside the
 //                                        frame, net:342-351) is a plain load.
-//   W     [K/16][N/16][4][16][4]         packed fp32 weights of one GEMM (see pack_weights in codec.hip)
+//   W     [K/16][N/16][4][16][4]         packed fp32 weights of one GEMM (see upload_layer in model.hip)
 //   acts  [rows][width]                  per-step activations, row = block (or block x position)
 #pragma once
 
@@ -18,7 +18,7 @@ constexpr int KSPLIT = 8;   // every GEMM output = ((s0 + s1) + ... + s7) + bias
                             // over the i-th eighth of K: identical for every tile shape, so the encoder
                             // (large wavefront M) and the decoder (M = n_img) compute bit-identical values.
 
-// SEG_L0TAP: a cell of the context net's layer-0 map cache (KS[1] = 3; codec.hip, "layer-0 map cache"), laid
+// SEG_L0TAP: a cell of the context net's layer-0 map cache (KS[1] = 3; model.hip, "Layer-0 map cache"), laid
 // out like zpad ([n_img][Hb+2][Wb+4] cells) with the layer-0 width per cell
 enum SegKind : int { SEG_DENSE = 0, SEG_ZTAP = 1, SEG_X = 2, SEG_L0TAP = 3 };
 // EPI_LEAKY_L0: LeakyReLU, written to the layer-0 map cache cell of the row's (block, position) instead of row-major
@@ -171,7 +171,7 @@ struct OneOp {             // (the epilogue's fields first: one scalar-cache lin
     int l0out;               // 1: the context net's layer 0 under the layer-0 cache (KS[1] = 3): every output also goes
                              // to the cache cell of its position, and at a row end a second position (h = 0: (v, -1);
                              // h = Wb - 1: (v - 1, Wb)) rides in MFMA row 1 (and 2 when Wb = 1) -- the graph decoder's
-                             // raster positions (codec.hip run_ctx)
+                             // raster positions (step.hip run_ctx)
     int half;                // 1: every column tile is held as two halves (K slices 0-3 / 4-7) by two workgroups (a
                              // whole tile would not fit one workgroup's LDS); half 0 hands its four slice partials over
                              // as granules `pgran` [2 step parities][N / 16][4][16], half 1 sums all eight in slice order

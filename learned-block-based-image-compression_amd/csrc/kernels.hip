@@ -263,11 +263,7 @@ constexpr int SMALL_MAX = 64, DEC_SMALL_MAX = 1024;
 // 0 = k_gemm_s (latency-shaped, any M; the decoder's raster steps stay on it when several batches are decoded
 // together: a raster step's latency barely grows with its rows), 1 = k_gemm (the encoder's wavefront steps)
 int gemm_class(const GemmArgs& g) {
-    static const int small_max = [] {      // experiment hook: LBIC_ENC_SMALL = largest M on k_gemm_s
-        const char* e = getenv("LBIC_ENC_SMALL");
-        return e ? atoi(e) : SMALL_MAX;
-    }();
-    return (g.M <= small_max || (g.raster && g.M <= DEC_SMALL_MAX)) ? 0 : 1;
+    return (g.M <= SMALL_MAX || (g.raster && g.M <= DEC_SMALL_MAX)) ? 0 : 1;
 }
 template <int BM, int BN, int NW, int CH, int OCC = 1>
 static int launch_cfg(const GemmArgs& g, hipStream_t s) {
@@ -370,15 +366,8 @@ int launch_gemm(const GemmArgs& g0, hipStream_t s, int* cfg_id) {
     // register caps that spill (64 / 80 VGPRs) 116.7 / 115.8.  Beside the team decoder (bench.py --steps 20):
     // 84.9 Mpix/s against 79.7 for the earlier default.  (Other tiles, XCD-aware and 2-D XCD tile orders: measured
     // in rounds 2-3 and removed)
-    static const int tile = [] {       // experiment hook: LBIC_ENC_TILE=1 -> 32 x 32 tiles (round 6, 128-frame passes)
-        const char* e = getenv("LBIC_ENC_TILE");
-        return e ? atoi(e) : 0;
-    }();
-    if (tile == 1) return launch_cfg<32, 32, 8, 1>(g, s);
-    if (tile == 2) return launch_cfg<16, 64, 8, 1>(g, s);
     return launch_cfg<16, 32, 8, 1>(g, s);
 }
-
 
 __global__ __launch_bounds__(RANS_WPB * 64) void k_rans_decode(const RansArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t lcdf[];
@@ -472,7 +461,7 @@ __global__ void k_fill_interior(const float* __restrict__ zin, float* __restrict
     }
 }
 
-// Layer-0 map cache (KS[1] = 3, codec.hip) before a closed loop: every channel of the cells of block row -1 (columns
+// Layer-0 map cache (KS[1] = 3, model.hip) before a closed loop: every channel of the cells of block row -1 (columns
 // -1 .. Wb) and of columns -1 and Wb of every block row set to LeakyReLU(bias) (compress(): layer 0 of the
 // zero-padded window, net:342-351, where every tap is zero) or to 0 (bias = null: forward()'s frame padding).  The
 // GEMM computes such a cell as (slice sums of zeros) + bias -> LeakyReLU, i.e. the same value.  Columns -1 / Wb

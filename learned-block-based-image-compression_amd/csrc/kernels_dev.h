@@ -245,7 +245,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, float v, int row, in
     }
 }
 
-// A / W fragments of one 16-wide k-block for this lane (operand maps: the packing comment in codec.hip)
+// A / W fragments of one 16-wide k-block for this lane (operand maps: upload_layer in model.hip)
 template <int MS, int NS>
 struct Frag {
     f4 a[MS];
@@ -953,6 +953,5 @@ __device__ __forceinline__ void rans_row_sparse(const RansArgs& a, uint32_t* lwi
     }
     RSTAMP(3);
 }
-
 
 }  // namespace lbic

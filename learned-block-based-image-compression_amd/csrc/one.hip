@@ -218,7 +218,7 @@ __device__ __forceinline__ bool one_gemm(const OneArgs& a, const OneOp& op, int 
     const int q4 = (lane >> 4) * 4;
     const long cell = ((long)(v + 2) * a.Wp + (h + 2));
     // the layer-0 op (l0out) at a row end: positions 1 (and 2) in MFMA rows 1 (2), the graph decoder's raster positions
-    // (codec.hip run_ctx): h = 0 adds (v, -1), h = Wb - 1 adds (v - 1, Wb)
+    // (step.hip run_ctx): h = 0 adds (v, -1), h = Wb - 1 adds (v - 1, Wb)
     const int P = L0 && op.l0out ? 1 + (h == 0 ? 1 : 0) + (h == a.Wb - 1 ? 1 : 0) : 1;
     const long cell1 = h == 0 ? cell - 1 : cell - a.Wp + 1, cell2 = cell - a.Wp + 1;
     const int prow = lane & 15;

@@ -335,7 +335,7 @@ def test_gang_decode_many_rows(name, n_img):
 
 @pytest.mark.parametrize("shape", [(8, 12), (5, 1), (1, 7), (6, 2)])
 def test_layer0_cache_equals_five_positions(shape, monkeypatch):
-    """KS[1] = 3: the context net's layer-0 map cache (codec.hip, computed once per block at its own step, border
+    """KS[1] = 3: the context net's layer-0 map cache (model.hip, computed once per block at its own step, border
     columns at the steps that own them) gives bit-identical symbols, indexes, bits and reconstructions to layer 0
     evaluated at the five positions of every block (LBIC_L0CACHE=0), for compress(), the raster and the wavefront
     (sub-stream) decoders and the validation loop's frame padding; ragged and one-block-wide frames included."""

@@ -5,7 +5,7 @@ zeroes its buffers and uploads its block lists -- while another thread captures 
 and replays encoder graphs of the first handle on a stream of its own.  Round 5 saw two failures of this class: a
 legacy-stream copy refused beside another thread's graph capture (e610271), and workspace zeroing on a non-blocking
 stream overtaking the handle's previous work still queued on the caller's stream (ed23e9a).  Workspace set-up now runs
-on a private stream of the handle, ordered after the caller's stream by an event (codec.hip ws_stream).  The decoding
+on a private stream of the handle, ordered after the caller's stream by an event (model.hip ws_stream).  The decoding
 thread runs once on a dedicated stream and once on torch's default stream (the legacy stream: what a multi-threaded
 caller that never sets a stream passes).  Every call must succeed, and every result must equal the same call made
 serially beforehand (encode bit for bit, decode == encode)."""

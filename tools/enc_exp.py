@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Encoder experiment: compress time of one batch of 32 B8_lowrate 768x768 frames (encoder alone, HIP events around
-the wavefront graph), and a digest of its symbols / indexes / zhat to compare kernel variants (LBIC_ENC_TILED ...)."""
+the wavefront graph), and a digest of its symbols / indexes / zhat to compare kernel variants (builds of the
+library loaded side by side with LBIC_LIB_VARIANT)."""
 import hashlib
 import json
 import os

@@ -1,12 +1,13 @@
 #!/bin/bash
 # PMC passes over the encoder alone (tools/enc_exp.py: one 32-frame B8_lowrate 768x768 batch, 4 compressions), for
-# the GEMM variant LBIC_ENC_TILED selects: MFMA busy, LDS bank conflicts, wave cycles.  Outputs under gpurun_out/.
+# the library build LBIC_LIB_VARIANT selects (the label $1 names the outputs): MFMA busy, LDS bank conflicts, wave
+# cycles.  Outputs go to the directory $O set below.
 set -eo pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 V=${1:-3}
 mkdir -p $O
-export TMPDIR=/tmp LBIC_ENC_TILED=$V
+export TMPDIR=/tmp
 cd /tmp
 rm -rf /tmp/ep1_$V /tmp/ep2_$V
 timeout -k 10 200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_LDS --output-format csv -d /tmp/ep1_$V -o run -- python3 $R/tools/enc_exp.py > $O/enc_pmc1_$V.log 2>&1
